@@ -17,10 +17,23 @@ C4: 100M tuples on 8 GPUs): 100M tuples in total, split over the ranks; --scalin
 --config C1..C5 runs one BASELINE configuration as the headline line instead:
   C1 MR-Dim 2D uniform 1M P=8 | C2 MR-Grid 4D correlated 10M P=8 | C3 MR-Angle 4D anti 50M P=8
   C4 MR-Angle 8D anti 100M P=16 | C5 6D mixed continuous queries, MR-Angle P=8.
-The default run (C4) also carries every other configuration as a sub-line under
-"configs" (each with its own roofline and cpu_baseline), the end-to-end C4 rates with the
-host->device transfer (rows, or CSV text) inside the timed region, and the companion
-rooflines of the dominance, CSV-decode and sort kernels.
+A plain run sets up, warms up, times --steps steps and prints the headline line (with the
+k_filter roofline, which comes out of the timed steps themselves).  --dump-outputs DIR also
+writes what the last timed step returned (below).  --full adds every measurement that takes
+runs of its own: the phase split of one more step, the CPU baseline, and for C4 every other
+configuration as a sub-line under "configs" (each with its own roofline and cpu_baseline), the
+end-to-end C4 rates with the host->device transfer (rows, or CSV text) inside the timed
+region, and the companion rooflines of the dominance, CSV-decode and sort kernels; with
+N > 1 the other scaling mode; with --config C5 the sliding-window stream.  The --no-* options
+drop single parts of a --full run.
+
+--dump-outputs DIR: after the timed steps, what the last timed step handed to its caller, as
+DIR/<name>.npy: skyline_size (f64[1]), skyline_ids (f64: the ids in stream order),
+skyline_origins (f32: their partitions), local_sizes and survivors (f64[K]: |L_k| and
+survivors_k).  A skyline of more than DUMP_MAX_ROWS tuples is written as a fixed sample: the
+rows at skyline_sample_index (f64), drawn once with a fixed seed.  The stream is generated
+from a fixed seed, so two builds given the same arguments can be compared array for array.
+With N > 1 every rank writes its own arrays as <name>_rank<r>.npy.
 
 "roofline": the dominant kernel (k_filter, HBM-bound), HIP events on the stream it is
 launched on.  "cpu_baseline": the C restatement of the reference operators (oracle/,
@@ -65,6 +78,10 @@ CONFIGS = {
 # the one published reference number for a configured workload: MR-Dim, 2D, 1M tuples,
 # TotalTime 19,544 ms (python/graph_paper_figures.py:29; hardware unstated)
 C1_PUBLISHED_MS = 19544.0
+# --dump-outputs: at most this many skyline rows (8-byte id + 8-byte index + 4-byte origin each:
+# 20 MB at the cap), a larger skyline is sampled with DUMP_SEED
+DUMP_MAX_ROWS = 1_000_000
+DUMP_SEED = 20261019
 
 
 def host_cores():
@@ -167,9 +184,32 @@ def make_stream(eng, dist_name, n, seed, id0, dev):
     return vals, ids
 
 
-def time_steps(step, eng, steps, warmup, distributed):
+def dump_outputs(out_dir, eng, g, out_ids, out_org, rank, world):
+    """--dump-outputs: the arrays the last step returned (see the module docstring)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    arrays = {"skyline_size": np.array([g], np.float64)}
+    if g > DUMP_MAX_ROWS:
+        idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, g, DUMP_MAX_ROWS))
+        sel = torch.from_numpy(idx).to(out_ids.device)
+        ids, org = out_ids[:g][sel], out_org[:g][sel]
+        arrays["skyline_sample_index"] = idx.astype(np.float64)
+    else:
+        ids, org = out_ids[:g], out_org[:g]
+    arrays["skyline_ids"] = ids.cpu().numpy().astype(np.float64)
+    arrays["skyline_origins"] = org.cpu().numpy().astype(np.float32)
+    ls, sv = eng.stats()
+    arrays["local_sizes"] = ls.astype(np.float64)
+    arrays["survivors"] = sv.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + sfx + ".npy"), a)
+
+
+def time_steps(step, eng, steps, warmup, distributed, phase_step=True, after_timed=None):
     """W untimed steps, then K timed steps with the light kernel timers on (HIP events around
-    the timed kernels only: the roofline), then one untimed step with the phase events on."""
+    the timed kernels only: the roofline); after_timed(g) then sees the last timed step's
+    outputs; phase_step: one more untimed step with the phase events on."""
     for _ in range(warmup):
         step()
     eng.sync()
@@ -192,9 +232,12 @@ def time_steps(step, eng, steps, warmup, distributed):
         dist.barrier()
     elapsed = time.perf_counter() - t0
     kt = eng.kernel_time("filter")   # the timed launches only
-    eng.profile(2)                   # phase split of one more (untimed) step
-    step()
-    eng.sync()
+    if after_timed is not None:
+        after_timed(g)
+    if phase_step:
+        eng.profile(2)               # phase split of one more (untimed) step
+        step()
+        eng.sync()
     eng.profile(False)
     return elapsed, step_ms, g, kt
 
@@ -776,6 +819,12 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", default="C4", choices=["C1", "C2", "C3", "C4", "C5"])
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: the phase split of one more step, the CPU "
+                         "baseline, the other configurations, the end-to-end, CSV, sort, operator-path and "
+                         "dominance companions, the other scaling mode (N > 1), the sliding-window stream (C5)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (see the module docstring)")
     ap.add_argument("--scaling", default="strong", choices=["weak", "strong"],
                     help="strong (default: BASELINE states each configuration's tuples in total, e.g. C4 = "
                          "100M tuples on 8 GPUs): --tuples in total, split over the ranks; weak: --tuples per "
@@ -801,6 +850,10 @@ def main():
                     help="nccl (= RCCL over xGMI, the measured path), gloo (rehearsing several ranks on one "
                          "GPU), auto: nccl when every rank has a GPU of its own")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.config == "C5":
+        ap.error("--dump-outputs writes a landmark-window query's outputs: not available with --config C5")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # one process per GPU: start the ranks from here, before anything touches the GPU
@@ -832,7 +885,7 @@ def main():
     if args.config == "C5":
         if rank == 0:
             lm = stream_run(dev_index, 1234 + 6)
-            sl = stream_run(dev_index, 1234 + 6, window=10_000_000)
+            sl = stream_run(dev_index, 1234 + 6, window=10_000_000) if args.full else None
             line = {"metric": METRIC, "value": lm["ingest_tuples_per_s"], "unit": "tuples/s", "n_gpus": 1,
                     "steps": 20, "warmup": 0, "ms_per_step": lm["p50_query_latency_ms"],
                     "p50_query_latency_ms": lm["p50_query_latency_ms"], "higher_is_better": True,
@@ -862,7 +915,7 @@ def main():
             return hi - lo, lo, n_cfg
         return n_cfg, rank * n_cfg, n_cfg * world
 
-    def measure(mode):
+    def measure(mode, dump_dir=None):
         """W + K steps of one scaling mode; every rank's elapsed / p50 reduced by MAX."""
         n, id0, total = shard(mode)
         vals, ids = make_stream(eng, cfg["dist"], n, seed, id0, dev)
@@ -877,7 +930,11 @@ def main():
                 return g
             return eng.query_dev(ids, vals, out_ids, out_org, n)
 
-        elapsed, step_ms, g, kt = time_steps(step, eng, args.steps, args.warmup, distributed)
+        dump = None
+        if dump_dir:
+            dump = lambda g_last: dump_outputs(dump_dir, eng, g_last, out_ids, out_org, rank, world)   # noqa: E731
+        elapsed, step_ms, g, kt = time_steps(step, eng, args.steps, args.warmup, distributed,
+                                             phase_step=args.full, after_timed=dump)
         p50 = statistics.median(step_ms)
         if distributed:
             t = torch.tensor([elapsed, p50], dtype=torch.float64, device=red_dev)
@@ -895,7 +952,7 @@ def main():
                     vals=vals, ids=ids, out_ids=out_ids, out_org=out_org)
 
     companion = None
-    if distributed and not args.no_companion_scaling:
+    if distributed and args.full and not args.no_companion_scaling:
         other = "weak" if args.scaling == "strong" else "strong"
         c = measure(other)
         ms_c = c["elapsed"] * 1e3 / args.steps
@@ -904,11 +961,11 @@ def main():
                      "tuples_total": c["total"], "skyline_size": c["g"], "dist_exchange": c["dist_stats"]}
         del c
         torch.cuda.empty_cache()
-    m = measure(args.scaling)
+    m = measure(args.scaling, args.dump_outputs)
     n, total, elapsed, step_ms, p50, g, kt = (m[k] for k in ("n", "total", "elapsed", "step_ms", "p50", "g", "kt"))
     vals, ids, out_ids, out_org = m["vals"], m["ids"], m["out_ids"], m["out_org"]
     dist_stats = m["dist_stats"]
-    phases, counters = eng.phases()
+    phases, counters = eng.phases() if args.full else (None, None)   # of the profiled extra step
     roof = filter_roofline(eng, D, kt)
 
     if rank == 0:
@@ -918,12 +975,12 @@ def main():
             roof["traffic"] = traffic_for(n, D, cfg["dist"])
         solo = world == 1
         cpu = None
-        if solo and not args.no_cpu_baseline:
+        if solo and args.full and not args.no_cpu_baseline:
             c = dict(cfg)
             c["tuples"] = n_cfg
             cpu = cpu_baseline(args.config, c, seed)
         extra = {}
-        if solo and args.config == "C4" and n_cfg == CONFIGS["C4"]["tuples"] and not args.dist:
+        if args.full and solo and args.config == "C4" and n_cfg == CONFIGS["C4"]["tuples"] and not args.dist:
             if not args.no_e2e:
                 extra["end_to_end"] = end_to_end_c4(eng, vals, ids, n, D, 3, out_ids, out_org)
             if not args.no_csv:
@@ -972,13 +1029,14 @@ def main():
                                      "RCCL over xGMI (nccl)" if backend == "nccl" else
                                      f"gloo rehearsal: {world} ranks on {min(n_dev, world)} GPU(s)")},
             "roofline": roof,
-            "phases_ms_last_step": phases,
-            "counters_last_step": {"n": int(counters[0]), "candidates": int(counters[1]),
-                                   "distinct_reps": int(counters[2]), "global_candidates": int(counters[3]),
-                                   "output": int(counters[4]), "sfs_rounds": int(counters[5])},
             "dist_exchange": dist_stats,
             "cpu_baseline": cpu,
         }
+        if args.full:
+            line["phases_ms_last_step"] = phases
+            line["counters_last_step"] = {"n": int(counters[0]), "candidates": int(counters[1]),
+                                          "distinct_reps": int(counters[2]), "global_candidates": int(counters[3]),
+                                          "output": int(counters[4]), "sfs_rounds": int(counters[5])}
         if companion is not None:
             line[f"{companion['scaling']}_scaling_companion"] = companion
         e2e = extra.get("end_to_end")

@@ -71,7 +71,7 @@ if [[ $STEPS == *fpmc* ]]; then
 fi
 if [[ $STEPS == *rehearse* ]]; then
   # two ranks on the one GPU over gloo (bench.py starts its own ranks): the per-step phase split
-  timeout -k 10 400 python -u bench.py --gpus 2 --steps 5 --warmup 2 > $OUT/rehearsal_$TAG.json 2> $OUT/rehearsal_$TAG.err || { tail -30 $OUT/rehearsal_$TAG.err; exit 1; }
+  timeout -k 10 400 python -u bench.py --full --gpus 2 --steps 5 --warmup 2 > $OUT/rehearsal_$TAG.json 2> $OUT/rehearsal_$TAG.err || { tail -30 $OUT/rehearsal_$TAG.err; exit 1; }
   cut -c1-600 $OUT/rehearsal_$TAG.json
 fi
 if [[ $STEPS == *csv* ]]; then
@@ -85,7 +85,7 @@ if [[ $STEPS == *probe* ]]; then
   cat $OUT/filter_probe_$TAG.log
 fi
 if [[ $STEPS == *bench* ]]; then
-  timeout -k 10 600 python -u bench.py ${BENCH_ARGS} > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err || { tail -30 $OUT/bench_$TAG.err; exit 1; }
+  timeout -k 10 600 python -u bench.py --full ${BENCH_ARGS} > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err || { tail -30 $OUT/bench_$TAG.err; exit 1; }
   cut -c1-1500 $OUT/bench_$TAG.json
 fi
 if [[ $STEPS == *dtrace* ]]; then
@@ -100,7 +100,7 @@ fi
 if [[ $STEPS == *ktrace* ]]; then
   export TMPDIR=/tmp
   rm -rf $OUT/trace_$TAG
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats -f csv -d $OUT/trace_$TAG -o run -- python3 -u $R/bench.py ${BENCH_ARGS} > $OUT/trace_$TAG.log 2>&1 || { tail -30 $OUT/trace_$TAG.log; exit 1; }
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats -f csv -d $OUT/trace_$TAG -o run -- python3 -u $R/bench.py --full ${BENCH_ARGS} > $OUT/trace_$TAG.log 2>&1 || { tail -30 $OUT/trace_$TAG.log; exit 1; }
   python tools/prof_summary.py trace $OUT/trace_$TAG > $OUT/trace_${TAG}_summary.txt
   head -30 $OUT/trace_${TAG}_summary.txt
 fi

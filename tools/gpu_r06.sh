@@ -33,7 +33,7 @@ for s in ${STEPS//,/ }; do
       timeout -k 10 1000 $PYT tests -m gpu > $OUT/pytest_gpu_$TAG.log 2>&1 || { tail -40 $OUT/pytest_gpu_$TAG.log; exit 1; }
       tail -3 $OUT/pytest_gpu_$TAG.log ;;
     bench)
-      timeout -k 10 500 python -u bench.py ${BENCH_ARGS} > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err || { tail -30 $OUT/bench_$TAG.err; exit 1; }
+      timeout -k 10 500 python -u bench.py --full ${BENCH_ARGS} > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err || { tail -30 $OUT/bench_$TAG.err; exit 1; }
       cut -c1-1500 $OUT/bench_$TAG.json ;;
     smoke)
       timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke_$TAG.log 2>&1 || { tail -30 $OUT/smoke_$TAG.log; exit 1; }
@@ -53,7 +53,7 @@ for s in ${STEPS//,/ }; do
       cat $OUT/traffic_filter_$TAG.json | head -20 ;;
     rehearse)
       timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-         --master-port 29517 bench.py --gpus 2 --steps 5 --warmup 2 --dist-backend gloo > $OUT/rehearsal2_$TAG.json 2> $OUT/rehearsal2_$TAG.err \
+         --master-port 29517 bench.py --full --gpus 2 --steps 5 --warmup 2 --dist-backend gloo > $OUT/rehearsal2_$TAG.json 2> $OUT/rehearsal2_$TAG.err \
          || { tail -30 $OUT/rehearsal2_$TAG.err; exit 1; }
       grep '^{' $OUT/rehearsal2_$TAG.json | cut -c1-300 ;;
     probe)
