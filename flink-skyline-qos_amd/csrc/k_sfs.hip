@@ -902,7 +902,7 @@ void launch_brute_pairs(int D, bool f32, bool u16, const void *rows, const uint6
     if (!mr) return;
     const dim3 g((mr + kBruteY - 1) / kBruteY, (mr + kBruteX - 1) / kBruteX);
     if (u16) {
-        // the large shape once it still fills the chip with >= 4096 workgroups (mr >= ~46k)
+        // the large shape once it still fills the chip with >= 4096 workgroups (mr >= 32257)
         const bool big = (uint64_t)((mr + 511) / 512) * ((mr + 511) / 512) >= 4096;
 #define SKY_B16(YL, X)                                                                                       \
     do {                                                                                                     \

@@ -265,8 +265,9 @@ struct sky_stream_landmark {
     sky::DevBuf rows2, key2, w2, tid2, trep2;   // the next state, swapped in after a query
     sky::DevBuf rowf, flag, pos, rflag, rpos, newrep, table, words, scratch;
     sky::DevBuf lb;                         // the query's one-pass scans' look-back words (scan_excl_u32_lb)
-    const void *lb_at = nullptr;            // ... the buffer zeroed last, and the last scan's epoch
-    uint32_t lb_epoch = 0;
+    const void *lb_at = nullptr;            // ... the buffer zeroed last (address and capacity: a regrown
+    size_t lb_cap = 0;                      //     buffer may come back at the same address), and the
+    uint32_t lb_epoch = 0;                  //     last scan's epoch
     int64_t R = 0, N = 0, T = 0, holes = 0;
     int64_t qcap = 0, tcap = 0;
 };
@@ -338,10 +339,11 @@ int lm_reserve(sky_stream *s, int64_t rows, int64_t tuples) {
     SKY_TRY(L.scratch.ensure(sky::scan_scratch_words(tn + 1) * 4 + 64));
     SKY_TRY(L.words.ensure(256));
     SKY_TRY(L.lb.ensure(sky::scan_lb_words(tn + 1) * 8));
-    if (L.lb.p != L.lb_at) {                  // new words: zeroed (no epoch yet), the error word too
+    if (L.lb.p != L.lb_at || L.lb.cap != L.lb_cap) {   // new words: zeroed (no epoch yet), the error word too
         HIP_TRY(hipMemsetAsync(L.lb.p, 0, L.lb.cap, c->st));
         HIP_TRY(hipMemsetAsync(L.words.as<uint32_t>() + 6, 0, 4, c->st));
         L.lb_at = L.lb.p;
+        L.lb_cap = L.lb.cap;
         L.lb_epoch = 0;
     }
     return SKY_OK;

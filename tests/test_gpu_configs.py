@@ -286,7 +286,7 @@ def test_radix_sort_at_scale(pattern, n, gpu_engine_factory):
     stable torch sort: keys sorted, values follow their keys, ties keep index order.
     'compressed_runs' spreads 28 varying bits over 7 bytes in 4 runs, so the order-preserving
     bit compression (k_rs_compress / k_rs_expand) is active: the regression case of commit
-    e3568d8 (corruption past ~65k keys).  16M keys use 4096-key tiles, 3M the 1024-key tiles
+    e3568d8 (corruption past ~65k keys).  16M keys use 6144-key tiles, 3M the 1024-key tiles
     of the query's candidate sorts."""
     eng = gpu_engine_factory(2, 4)
     g = torch.Generator(device="cuda")

@@ -192,3 +192,91 @@ def test_stream_query_async_then_wait(gpu_engine_factory, oracle, W):
     assert st.wait() == 0.0                         # nothing pending
     st.close()
     eng.close()
+
+
+# ---- the landmark query's look-back scans over many tiles (k_scan_lb, 4096 items per tile) --------
+def _lm_check(st, eng, which, m, keys, P_):
+    """One query of a stream_cases stream (ids 0..n-1 in arrival order, `which` the vector of each
+    tuple, `keys` the partition of each vector): ids in order, origins, stats and the resident count."""
+    import stream_cases as sc
+    ids_e, ls_e, sv_e = sc.expected(sc_vectors()[:m], sc.members(which, m), keys[:m], P_)
+    got, org = st.query()
+    np.testing.assert_array_equal(got, ids_e)
+    np.testing.assert_array_equal(org, keys[which[ids_e]])
+    ls, sv = eng.stats()
+    np.testing.assert_array_equal(ls, ls_e)
+    np.testing.assert_array_equal(sv, sv_e)
+    assert st.size() == (int(ls_e.sum()), len(which))      # the local skylines stay resident
+    return len(ids_e)
+
+
+def sc_vectors():
+    import stream_cases as sc
+    return np.vstack([sc.VECTORS, sc.B_KILLER])
+
+
+@pytest.mark.parametrize("n0", [16385, 262145, 270337])
+def test_landmark_lookback_scans_over_many_tiles(gpu_engine_factory, n0):
+    """The landmark query's three scans run k_scan_lb above 16384 elements; the golden streams (3000
+    tuples) never reach it and the C5 batches stay near 22 tiles.  Here almost every tuple is in the
+    skyline (three mutually non-dominating vectors), so every tile's total is large and a wrong
+    prefix in any tile moves thousands of ids.  n0 = 16385: the first size on k_scan_lb (5 tiles);
+    262145: 65 tiles, the last one looks back over exactly 64; 270337: 67 tiles, tiles 65 and 66
+    can go on to a second 64-tile window.  Then the same scans over [resident ; new], a 0/1 flag
+    pattern over every tile once one row has taken B's tuples out, and the compacted next state
+    read by one more query."""
+    import skyline
+    import stream_cases as sc
+    P_ = 8
+    eng = gpu_engine_factory(2, P_, "mr-angle")
+    vectors = sc_vectors()
+    keys = eng.partition_keys(vectors)
+    assert len(set(keys[:3].tolist())) == 3
+    assert keys[3] == keys[1], "the row that dominates B must share B's partition: choose another factor"
+    st = skyline.SkylineStream(eng, 0)
+    rng = np.random.default_rng(n0)
+    which = np.zeros(0, np.int64)
+
+    def append(w):
+        nonlocal which
+        ids = np.arange(len(which), len(which) + len(w), dtype=np.int64)
+        st.append(ids, vectors[w])
+        which = np.concatenate([which, w])
+
+    append(sc.draw(rng, n0))                                # 1. one batch, T = 0
+    assert _lm_check(st, eng, which, 3, keys, P_) == n0
+    append(sc.draw(rng, 20000))                             # 2. scans over [resident ; new]
+    assert _lm_check(st, eng, which, 3, keys, P_) == n0 + 20000
+    append(np.array([3]))                                   # 3. B's tuples leave L_k and the output
+    assert _lm_check(st, eng, which, 4, keys, P_) == int((which != 1).sum())
+    append(sc.draw(rng, 5000, among=(0, 2)))                # 4. the compacted state, read again
+    assert _lm_check(st, eng, which, 4, keys, P_) == int((which != 1).sum())
+    st.close()
+    eng.close()
+
+
+def test_landmark_state_regrows_across_queries(gpu_engine_factory):
+    """A stream that doubles between queries, 2e4 -> 6.4e5 resident tuples: every step regrows the
+    row and tuple buffers and with them the look-back words, while the scans' epoch is still small
+    (the words of a regrown buffer must read as 'no epoch yet': lm_reserve zeroes them whenever
+    the buffer's address or capacity changed).  A test cannot make the allocator hand the regrown
+    buffer back at its old address, which is the case the capacity check is for; this runs the
+    regrowth path at every size and checks every answer."""
+    import skyline
+    import stream_cases as sc
+    P_ = 8
+    eng = gpu_engine_factory(2, P_, "mr-angle")
+    vectors = sc_vectors()
+    keys = eng.partition_keys(vectors)
+    assert len(set(keys[:3].tolist())) == 3
+    st = skyline.SkylineStream(eng, 0)
+    rng = np.random.default_rng(64)
+    which = np.zeros(0, np.int64)
+    for b in (20000, 20000, 40000, 80000, 160000, 320000):
+        w = sc.draw(rng, b)
+        st.append(np.arange(len(which), len(which) + b, dtype=np.int64), vectors[w])
+        which = np.concatenate([which, w])
+        assert _lm_check(st, eng, which, 3, keys, P_) == len(which)
+    assert len(which) == 640000
+    st.close()
+    eng.close()
